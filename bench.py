@@ -4,10 +4,27 @@
 One step = one pass of the hot path over one synthetic input already
 resident in HBM.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what the
+headline figure needs: it builds the seeded input, warms up, calibrates
+--pipeline, times the K steps and prints the line with value and
+ms_per_step.  Everything else below -- other_configs, cpu_baseline, the
+bit-exact check against the oracle, and the passes made after the timed
+region (step_ms, ms_per_step_serial at two in flight, roofline,
+cold_single_decode, the slots' agreement) -- is measured only under --full;
+a plain line carries null in those places.
+
+--dump-outputs DIR writes, after the timed steps, what the last of them
+decoded: DIR/pcm.npy (float32; the whole PCM up to 8Mi samples, else the
+samples at 8Mi seeded positions, the same in every run), DIR/pcm_checksum.npy
+(the position-weighted 64-bit checksum of the whole PCM, per stream, as four
+16-bit limbs in float64) and DIR/status.npy (first error and exit state; C5:
+first_error.npy, per stream).  The input is a function of the arguments
+alone, so two builds can be compared array for array.
+
 N = 1 (default): BASELINE config C3 -- one 8-bit stereo stream of 5,000,000
 effective blocks (320M int16 samples), profile mix A, decoded by
-bjxa_hip_decode_async (speculative decode + verify/repair/tail).  The same
-run measures, under "other_configs": C2 (one 8-bit mono stream of 10M
+bjxa_hip_decode_async (speculative decode + verify/repair/tail).  A --full
+run also measures, under "other_configs": C2 (one 8-bit mono stream of 10M
 blocks), C4 (1024 mixed-format streams per launch), C5 (the whole 1024-stream
 job on this GPU: the N = 1 point of the scaling curve), C5g (one GPU's share
 of C5 at 8 GPUs) and the encode direction on C3-shaped PCM, each in a child
@@ -261,6 +278,52 @@ def pcm_checksum_torch(buf_u8, n):
     return int((x * w).sum().item())
 
 
+# ---- --dump-outputs ------------------------------------------------------------
+
+DUMP_SEED = 0xD0D0
+DUMP_MAX_SAMPLES = 8 << 20      # float32 PCM samples per rank: 32 MiB
+
+
+def dump_positions(n, k, seed):
+    """The positions of an n-sample output that --dump-outputs keeps: all of
+    them (None) when n <= k, else k drawn with a generator seeded by `seed`
+    alone, sorted -- the same positions in every run and every build."""
+    if n <= k:
+        return None
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return np.sort(rng.integers(0, n, k))
+
+
+def pcm_sample(buf, n, k, seed):
+    """float32 copy of the first n int16 samples of `buf` (a device byte
+    buffer or a host int16 array) at dump_positions(n, k, seed)."""
+    pos = dump_positions(n, k, seed)
+    if isinstance(buf, np.ndarray):
+        x = buf[:n]
+        return (x if pos is None else x[pos]).astype(np.float32)
+    import torch
+    x = buf[:2 * n].view(torch.int16)
+    if pos is not None:
+        x = x[torch.from_numpy(pos).to(x.device)]
+    return x.to(torch.float32).cpu().numpy()
+
+
+def checksum_limbs(sums):
+    """64-bit checksums as rows of four 16-bit limbs (low first) in float64,
+    which holds each limb exactly."""
+    u = np.array([s & 0xFFFFFFFFFFFFFFFF for s in sums], dtype=np.uint64).reshape(-1, 1)
+    return ((u >> np.arange(0, 64, 16, dtype=np.uint64)) & np.uint64(0xFFFF)).astype(np.float64)
+
+
+def write_dump(path, arrays, rank=0, world=1):
+    """--dump-outputs: DIR/<name>.npy for every array of this rank (at
+    N > 1, <name>.rank<r>.npy)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, name + ("" if world == 1 else ".rank%d" % rank) + ".npy"), a)
+
+
 # ---- one long stream per rank (C2/C3) ----------------------------------------
 
 def timed_serial(step, steps, dev):
@@ -275,10 +338,11 @@ def timed_serial(step, steps, dev):
     return time.perf_counter() - t0
 
 
-def timed_region(step, steps, depth, slots, dev):
+def timed_region(step, steps, depth, slots, dev, spread_pass=True):
     """The timed region: `steps` steps (consecutive slots when depth > 1,
     else slot 0), bracketed by a barrier (N > 1) and device synchronizes,
-    and nothing else on the streams.  Then the same steps once more with a
+    and nothing else on the streams.  Then (`spread_pass`, --full) the same
+    steps once more with a
     hipEvent pair recorded around each on its slot's stream, untimed, for
     the spread of the steps: an event between two steps costs the step
     after it ~4 % on C3 (tools/window_probe.py), which is
@@ -297,6 +361,8 @@ def timed_region(step, steps, depth, slots, dev):
     elapsed = time.perf_counter() - t0
     if dist_on():
         dist.barrier()
+    if not spread_pass:
+        return elapsed, []
     evs = EventPairs(steps)
     rec = evs.hip.hipEventRecord
     for i in range(steps):
@@ -441,9 +507,15 @@ def run_workload(name, args, dev, world, rank, verify, cpu_leg):
     for i in range(args.warmup):
         step(i)
     depth, cal = choose_depth(step, len(slots), dev, args.pipeline)
-    elapsed, step_ms = timed_region(step, args.steps, depth, slots, dev)
+    elapsed, step_ms = timed_region(step, args.steps, depth, slots, dev, args.full)
+    # the slot the last timed step decoded into.  Every later pass decodes
+    # the same input into the same buffers, so what --dump-outputs reads at
+    # the end is what that step wrote.
+    last = slots[(args.steps - 1) % len(slots) if depth > 1 else 0]
 
-    serial = timed_serial(step, args.steps, dev) if depth > 1 else elapsed
+    serial = elapsed
+    if depth > 1:
+        serial = timed_serial(step, args.steps, dev) if args.full else None
     # diagnostic (BJXA_BENCH_RECAL=1): the calibration once more after the
     # timed loops, to tell drift over the run from the window itself
     recal = None
@@ -463,24 +535,36 @@ def run_workload(name, args, dev, world, rank, verify, cpu_leg):
             seq.append(("loop", round((time.perf_counter() - t0) / args.steps * 1e3, 4)))
         recal["interleaved"] = seq
 
-    # kernel timing: slot 0 alone, one launch at a time (no overlap)
-    evs = EventPairs(max(EV_SAMPLES, args.steps))
-    for ev in evs.ev:
-        step(0, ev)
-    spec_ms = evs.ms()
-    evs.close()
+    # kernel timing (--full): slot 0 alone, one launch at a time (no overlap)
+    spec_ms = None
+    if args.full:
+        evs = EventPairs(max(EV_SAMPLES, args.steps))
+        for ev in evs.ev:
+            step(0, ev)
+        spec_ms = evs.ms()
+        evs.close()
     torch.cuda.synchronize(dev)
-    cold = cold_single(step, dev) if rank == 0 else None
+    cold = cold_single(step, dev) if rank == 0 and args.full else None
     st = slots[0]["status"].cpu().numpy().view(np.uint32).copy()
     # every slot's PCM and the status words the API defines (first error,
     # exit state, plan) equal slot 0's; the repair counters (words 3, 4)
     # may differ: whether a wave's boundary is repaired inside K1 or by the
     # tail depends on timing when other kernels share the GPU
     st0 = slots[0]["status"].cpu().numpy().view(np.uint32)
-    same = all(torch.equal(sl["dst"], slots[0]["dst"]) and
-               all(int(a) == int(b) for i, (a, b) in enumerate(zip(
-                   sl["status"].cpu().numpy().view(np.uint32), st0)) if i not in (3, 4))
-               for sl in slots[1:])
+    same = None
+    if args.full:
+        same = all(torch.equal(sl["dst"], slots[0]["dst"]) and
+                   all(int(a) == int(b) for i, (a, b) in enumerate(zip(
+                       sl["status"].cpu().numpy().view(np.uint32), st0)) if i not in (3, 4))
+                   for sl in slots[1:])
+    dump = None
+    if args.dump_outputs:
+        # the PCM a caller receives, and the status words that are results
+        # (first error, exit state L and R); the others say how the decode
+        # was planned and repaired, which depends on tuning and timing
+        dump = {"pcm": pcm_sample(last["dst"], samples, DUMP_MAX_SAMPLES, DUMP_SEED),
+                "pcm_checksum": checksum_limbs([pcm_checksum_torch(last["dst"], samples)]),
+                "status": last["status"].cpu().numpy().view(np.uint32)[:3].astype(np.float64)}
 
     ok, cpu, exact = None, None, None
     if verify or cpu_leg:
@@ -514,10 +598,11 @@ def run_workload(name, args, dev, world, rank, verify, cpu_leg):
     return {"name": name, "desc": desc, "eb": eb, "bits": bits, "ch": ch, "samples": samples,
             "elapsed": elapsed, "serial": serial, "pipeline": depth, "pipeline_cal": cal,
             "recal": recal,
-            "step_ms": spread(step_ms, depth), "spec_ms": float(np.median(spec_ms)),
-            "spec_samples": len(spec_ms), "status": st, "xa_bytes": xa_bytes,
+            "step_ms": spread(step_ms, depth),
+            "spec_ms": float(np.median(spec_ms)) if spec_ms else None,
+            "spec_samples": len(spec_ms or ()), "status": st, "xa_bytes": xa_bytes,
             "alg_bytes": xa_bytes + eb * 64 * ch, "ok": ok, "pcm_equal_oracle": exact,
-            "slots_agree": same, "cpu": cpu, "cold": cold}
+            "slots_agree": same, "cpu": cpu, "cold": cold, "dump": dump}
 
 
 COLD_PAUSE_S = 0.010
@@ -657,11 +742,12 @@ def cpu_batch_baseline(name, inputs):
 
 
 def run_batch(name, steps, warmup, dev, verify, nstreams=0, rank=0, world=1, eblocks=0,
-              cpu_leg=False, bad_stream=-1, pipeline=1, variant=0):
+              cpu_leg=False, bad_stream=-1, pipeline=1, variant=0, full=True, dump=False):
     """Decode (this rank's share of) a batch config with bjxa_hip_batch_* --
     all streams per launch -- `steps` times after `warmup` untimed steps,
-    then time EV_SAMPLES more launches with events.  Returns this rank's
-    measurements incl. per-stream checksums and first failing stream."""
+    then (`full`) time EV_SAMPLES more launches with events.  Returns this
+    rank's measurements incl. per-stream checksums and first failing stream,
+    and (`dump`) the --dump-outputs arrays."""
     import torch
     import torch.distributed as dist
     import bjxa_amd
@@ -705,24 +791,49 @@ def run_batch(name, steps, warmup, dev, verify, nstreams=0, rank=0, world=1, ebl
             for i in range(warmup):
                 step(i)
             depth, cal = choose_depth(step, len(slots), dev, pipeline)
-            elapsed, step_ms = timed_region(step, steps, depth, slots, dev)
-            serial = timed_serial(step, steps, dev) if depth > 1 else elapsed
-            # kernel timing: slot 0 alone, one launch at a time
-            evs = EventPairs(max(EV_SAMPLES, steps))
-            for ev in evs.ev:
-                step(0, ev)
-            spec = evs.ms()
-            evs.close()
+            elapsed, step_ms = timed_region(step, steps, depth, slots, dev, full)
+            serial = elapsed
+            if depth > 1:
+                serial = timed_serial(step, steps, dev) if full else None
+            # kernel timing (--full): slot 0 alone, one launch at a time
+            if full:
+                evs = EventPairs(max(EV_SAMPLES, steps))
+                for ev in evs.ev:
+                    step(0, ev)
+                spec = evs.ms()
+                evs.close()
             torch.cuda.synchronize(dev)
     elif dist_on():
         dist.barrier()
         dist.barrier()
-    dsts, status = slots[0]["dsts"], slots[0]["status"]
-    spec_ms = float(np.median(spec))
-    st = status.cpu().numpy().view(np.uint32).reshape(max(n, 1), -1)[:n]
-    # a failed stream counts only the PCM before its failing eblock
-    valid = [eb * 32 * ch if int(w[0]) == NO_ERROR else int(w[0]) // ch * 32 * ch
-             for (_, _, ch, eb, _), w in zip(inputs, st)]
+    dsts = slots[0]["dsts"]
+    spec_ms = float(np.median(spec)) if full else None
+
+    def status_words(sl):
+        return sl["status"].cpu().numpy().view(np.uint32).reshape(max(n, 1), -1)[:n]
+
+    def valid_samples(words):
+        """a failed stream counts only the PCM before its failing eblock"""
+        return [eb * 32 * ch if int(w[0]) == NO_ERROR else int(w[0]) // ch * 32 * ch
+                for (_, _, ch, eb, _), w in zip(inputs, words)]
+    st = status_words(slots[0])
+    valid = valid_samples(st)
+    arrays = None
+    if dump:
+        # what the last timed step left in its slot (every later pass decodes
+        # the same inputs into the same buffers): of every stream the PCM
+        # before its first error and the first error itself; one seeded
+        # sample per stream, by its index in the whole job
+        last = slots[(steps - 1) % len(slots) if depth > 1 else 0]
+        lw = status_words(last)
+        lv = valid_samples(lw)
+        k = max(1, DUMP_MAX_SAMPLES // max(n, 1))
+        parts = [pcm_sample(d, v, k, DUMP_SEED + i)
+                 for (i, *_), d, v in zip(inputs, last["dsts"], lv)]
+        arrays = {"pcm": np.concatenate(parts) if parts else np.zeros(0, np.float32),
+                  "pcm_checksum": checksum_limbs([pcm_checksum_torch(d, v)
+                                                  for d, v in zip(last["dsts"], lv)]),
+                  "first_error": lw[:, 0].astype(np.float64) if n else np.zeros(0)}
 
     def agrees(sl):
         """Slot sl's results equal slot 0's where the API defines them: the
@@ -730,12 +841,12 @@ def run_batch(name, steps, warmup, dev, verify, nstreams=0, rank=0, world=1, ebl
         state.  The chunk plan (and with it the repair counts, and the PCM
         and state past an error) may differ between slots: the packed-layout
         plan depends on where each slot's buffers sit."""
-        s2 = sl["status"].cpu().numpy().view(np.uint32).reshape(max(n, 1), -1)[:n]
+        s2 = status_words(sl)
         return all(int(a[0]) == int(w[0]) and (int(w[0]) != NO_ERROR or
                                                tuple(a[1:3]) == tuple(w[1:3])) and
                    torch.equal(x[:2 * v], y[:2 * v])
                    for a, w, x, y, v in zip(s2, st, sl["dsts"], dsts, valid))
-    same = all(agrees(sl) for sl in slots[1:])
+    same = all(agrees(sl) for sl in slots[1:]) if full else None
     sums = [pcm_checksum_torch(d, v) for d, v in zip(dsts, valid)]
     first_err = min([i for (i, *_), w in zip(inputs, st) if int(w[0]) != NO_ERROR],
                     default=FIRST_ERR_NONE)
@@ -760,13 +871,15 @@ def run_batch(name, steps, warmup, dev, verify, nstreams=0, rank=0, world=1, ebl
             "unit": "MSamples/s",
             "ms_per_step": round(elapsed / steps * 1e3, 4), "step_ms": spread(step_ms, depth),
             "pipeline": depth, "pipeline_cal": cal,
-            "ms_per_step_serial": round(serial / steps * 1e3, 4),
-            "spec_ms": round(spec_ms, 4), "spec_samples": len(spec),
-            "frac": round(alg / (spec_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if spec_ms else 0.0,
+            "ms_per_step_serial": None if serial is None else round(serial / steps * 1e3, 4),
+            "spec_ms": None if spec_ms is None else round(spec_ms, 4),
+            "spec_samples": len(spec) if full else 0,
+            "frac": (None if spec_ms is None else
+                     round(alg / (spec_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if spec_ms else 0.0),
             "alg_bytes": alg, "repaired": int(st[:, 3].sum()) if n else 0,
             "tail": int(st[:, 4].sum()) if n else 0, "chunks": int(st[:, 5].sum()) if n else 0,
             "bit_exact": ok, "checksums": sums, "ref_checksums": ref_sums,
-            "first_error": first_err, "cpu_baseline": cpu}
+            "first_error": first_err, "cpu_baseline": cpu, "dump": arrays}
 
 
 def run_encode(steps, warmup, dev, verify, cpu_leg=False):
@@ -888,14 +1001,31 @@ def parse_args(argv=None):
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-other", action="store_true",
                     help="skip the other_configs lines")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the other_configs "
+                         "lines, the CPU baselines, the bit-exact check against the "
+                         "oracle, and the passes after the timed region (per-step "
+                         "spread, one-at-a-time steps, kernel times for the roofline, "
+                         "cold single decode, slot agreement); --no-cpu, --no-verify "
+                         "and --no-other take their parts out again")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them decoded "
+                         "to DIR/<name>.npy (float32/float64; a fixed seeded sample of "
+                         "a large output)")
     ap.add_argument("--only-other", default=None, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.only_other:
+        args.full = True        # an other_configs line exists only under --full
+    if not args.full:
+        # a plain run does what its headline figure needs and nothing else
+        args.no_cpu = args.no_verify = args.no_other = True
+    return args
 
 
 def other_child(name, args):
     """other_configs[name], measured by a child bench.py (--only-other) in a
     process of its own; the parent has not touched the GPU yet."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--only-other", name,
+    cmd = [sys.executable, os.path.abspath(__file__), "--only-other", name, "--full",
            "--steps", str(args.steps), "--warmup", str(args.warmup), "--mix", args.mix,
            "--pipeline", str(args.pipeline)]
     cmd += ["--no-cpu"] if args.no_cpu else []
@@ -925,7 +1055,7 @@ def only_other(args):
         o = run_batch(name, args.steps, args.warmup, dev, verify, cpu_leg=cpu_leg,
                       variant=args.variant,
                       pipeline=args.pipeline)
-        for k in ("checksums", "ref_checksums", "shard"):
+        for k in ("checksums", "ref_checksums", "shard", "dump"):
             o.pop(k)
         if o["first_error"] == FIRST_ERR_NONE:
             o["first_error"] = None
@@ -992,6 +1122,7 @@ def main():
 
 
 def other_stream_line(o, steps, world=1):
+    """An other_configs line of a --full run (every pass was made)."""
     return {"workload": o["desc"] + (" per rank" if world > 1 else ""),
             "value": round(job_value(o["samples"], world, steps, o["elapsed"]), 1),
             "unit": "MSamples/s", "ms_per_step": round(o["elapsed"] / steps * 1e3, 4),
@@ -1019,10 +1150,25 @@ def main_stream(args, workload, dev, world, rank, others=None):
         exact = o.get("bit_exact", o.get("byte_exact"))
         ok = ok if exact in (None, True) else False
 
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, r["dump"], rank, world)
+
     st = r["status"]
-    achieved = r["alg_bytes"] / (r["spec_ms"] * 1e-3) / 1e9
-    read_gbs = r["xa_bytes"] / (r["spec_ms"] * 1e-3) / 1e9
-    traffic, traffic_src = pmc_traffic(workload, args.mix)
+    roofline = None
+    if r["spec_ms"]:        # --full: the kernel-timing pass was made
+        achieved = r["alg_bytes"] / (r["spec_ms"] * 1e-3) / 1e9
+        read_gbs = r["xa_bytes"] / (r["spec_ms"] * 1e-3) / 1e9
+        traffic, traffic_src = pmc_traffic(workload, args.mix)
+        roofline = {"bound": "hbm", "kernel": "xa_decode_spec",
+                    "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                    "alg_bytes_per_launch": r["alg_bytes"], "traffic_source": traffic_src,
+                    "read_only_achieved": round(read_gbs, 1),
+                    "read_only_frac": round(read_gbs / HBM_PEAK_GBS, 4),
+                    "launch_ms": round(r["spec_ms"], 4),
+                    "launch_ms_stat": "median of %d launches" % r["spec_samples"],
+                    "step_frac": round(r["alg_bytes"] / (elapsed / args.steps) / 1e9 /
+                                       HBM_PEAK_GBS / world, 4)}
     line = {
         "metric": METRIC,
         "value": round(job_value(r["samples"], world, args.steps, elapsed), 1),
@@ -1031,7 +1177,9 @@ def main_stream(args, workload, dev, world, rank, others=None):
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "ms_per_step_serial": round(r["serial"] / args.steps * 1e3, 4),
+        "full": args.full,
+        "ms_per_step_serial": (None if r["serial"] is None else
+                               round(r["serial"] / args.steps * 1e3, 4)),
         "step_ms": r["step_ms"],
         "cold_single_decode": r["cold"],
         "higher_is_better": True,
@@ -1047,16 +1195,7 @@ def main_stream(args, workload, dev, world, rank, others=None):
                    "tuning": "auto" if not args.chunk and args.warm_blocks < 0 else "manual",
                    "pipeline": r["pipeline"], "pipeline_cal": r["pipeline_cal"],
                    **({"recal": r["recal"]} if r.get("recal") else {})},
-        "roofline": {"bound": "hbm", "kernel": "xa_decode_spec",
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "alg_bytes_per_launch": r["alg_bytes"], "traffic_source": traffic_src,
-                     "read_only_achieved": round(read_gbs, 1),
-                     "read_only_frac": round(read_gbs / HBM_PEAK_GBS, 4),
-                     "launch_ms": round(r["spec_ms"], 4),
-                     "launch_ms_stat": "median of %d launches" % r["spec_samples"],
-                     "step_frac": round(r["alg_bytes"] / (elapsed / args.steps) / 1e9 /
-                                        HBM_PEAK_GBS / world, 4)},
+        "roofline": roofline,
         "cpu_baseline": r["cpu"],
         "bit_exact": ok,
         "repaired_chunks": int(st[3]), "tail_repairs": int(st[4]), "chunks": int(st[5]),
@@ -1125,7 +1264,10 @@ def main_c5(args, dev, world, rank, cdev=None):
     cdev = cdev or dev
     nstreams = args.streams or 1024
     r = run_batch("C5", args.steps, args.warmup, dev, not args.no_verify, nstreams, rank,
-                  world, args.eblocks, bad_stream=args.bad_stream, pipeline=args.pipeline)
+                  world, args.eblocks, bad_stream=args.bad_stream, pipeline=args.pipeline,
+                  full=args.full, dump=bool(args.dump_outputs))
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, r["dump"], rank, world)
     elapsed, ok = r["elapsed"], r["bit_exact"]
     if dist_on():
         elapsed, ok = reduce_over_ranks(elapsed, ok, cdev)
@@ -1133,16 +1275,26 @@ def main_c5(args, dev, world, rank, cdev=None):
     digest, match = checksum_report(job)
     if match is False:
         ok = False
-    # per-rank kernel times for the report
+    # per-rank kernel times for the report (--full: the kernel-timing pass)
     import torch
     import torch.distributed as dist
-    lm = torch.tensor([r["spec_ms"], r["frac"]], dtype=torch.float64, device=cdev)
-    parts = [torch.zeros_like(lm) for _ in range(world)]
-    if dist_on():
-        dist.all_gather(parts, lm)
-    else:
-        parts = [lm]
-    per_rank = [[round(float(p[0]), 4), round(float(p[1]), 4)] for p in parts]
+    roofline = None
+    if args.full:
+        lm = torch.tensor([r["spec_ms"], r["frac"]], dtype=torch.float64, device=cdev)
+        parts = [torch.zeros_like(lm) for _ in range(world)]
+        if dist_on():
+            dist.all_gather(parts, lm)
+        else:
+            parts = [lm]
+        per_rank = [[round(float(p[0]), 4), round(float(p[1]), 4)] for p in parts]
+        spec_ms = r["spec_ms"]
+        roofline = {"bound": "hbm", "kernel": "xa_decode_spec_batch (rank 0)",
+                    "achieved": round(r["alg_bytes"] / (spec_ms * 1e-3) / 1e9, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": r["frac"],
+                    "traffic": None, "alg_bytes_per_launch": r["alg_bytes"],
+                    "launch_ms": spec_ms,
+                    "launch_ms_stat": "median of %d launches" % r["spec_samples"],
+                    "per_rank_launch_ms_frac": per_rank}
 
     other = {}
     if not args.no_other and world > 1:
@@ -1153,11 +1305,10 @@ def main_c5(args, dev, world, rank, cdev=None):
         other["C3_weak"] = other_stream_line(o, args.steps, world)
         ok = ok if ok3 in (None, True) else False
 
-    spec_ms = r["spec_ms"]
     line = {
         "metric": METRIC,
         "value": round(job["samples"] * args.steps / elapsed / 1e6, 1), "unit": "MSamples/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "ms_per_step_serial": r["ms_per_step_serial"], "step_ms": r["step_ms"],
         "higher_is_better": True,
@@ -1175,13 +1326,7 @@ def main_c5(args, dev, world, rank, cdev=None):
                                      "this same job on one GPU, the first point of the "
                                      "strong-scaling curve (the N = 1 headline itself is "
                                      "C3, one stream)"},
-        "roofline": {"bound": "hbm", "kernel": "xa_decode_spec_batch (rank 0)",
-                     "achieved": round(r["alg_bytes"] / (spec_ms * 1e-3) / 1e9, 1),
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": r["frac"],
-                     "traffic": None, "alg_bytes_per_launch": r["alg_bytes"],
-                     "launch_ms": spec_ms,
-                     "launch_ms_stat": "median of %d launches" % r["spec_samples"],
-                     "per_rank_launch_ms_frac": per_rank},
+        "roofline": roofline,
         "cpu_baseline": None, "bit_exact": ok,
         "control_plane": {"shards": job["shards"], "samples": job["samples"],
                           "repaired_chunks": job["repaired"], "tail_repairs": job["tail"],
@@ -1233,6 +1378,12 @@ def main_c5_cpu(args, dev, world, rank):
                         pcms[i] = pcm[:bad * 32 * ch]
     elapsed = time.perf_counter() - t0
     sums = [pcm_checksum_np(pcms[i]) for i, *_ in inputs]
+    if args.dump_outputs:
+        k = max(1, DUMP_MAX_SAMPLES // max(len(inputs), 1))
+        parts = [pcm_sample(pcms[i], pcms[i].size, k, DUMP_SEED + i) for i, *_ in inputs]
+        write_dump(args.dump_outputs,
+                   {"pcm": np.concatenate(parts) if parts else np.zeros(0, np.float32),
+                    "pcm_checksum": checksum_limbs(sums)}, rank, world)
     ok, refs = None, None
     if not args.no_verify:
         ref, _ = oracle_batch(inputs, 1)

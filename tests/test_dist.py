@@ -214,14 +214,17 @@ def test_single_stream_split(world, eb, bits, ch, mix, warmup, bad):
         assert any(r[3] > 1 for r in res)      # some rank had to re-decode
 
 
-def _bench(args, env_extra=None, timeout=240):
+def _bench(args, env_extra=None, timeout=240, full=True):
+    """bench.py over gloo on CPU, with --full (the check against the oracle)
+    unless `full` is False: a plain run."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BJXA_BENCH_BACKEND="gloo", HIP_VISIBLE_DEVICES="-1")
     env.update(env_extra or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] +
+                       (["--full"] if full else []) + args,
                        capture_output=True, text=True, env=env, timeout=timeout)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     return r.returncode, (json.loads(lines[-1]) if lines else None), r.stderr
@@ -292,3 +295,53 @@ def test_bench_force_pg_one_rank():
     cp = line["control_plane"]
     assert cp["shards"] == [[0, 6]] and cp["first_error_stream"] == 4
     assert cp["checksums_match_oracle"] is True and line["bit_exact"] is True
+
+
+def test_dump_positions_and_limbs():
+    """--dump-outputs keeps a short output whole and of a long one the same
+    sorted positions in every run; a checksum survives its float64 limbs."""
+    import bench
+    assert bench.dump_positions(100, 100, 1) is None
+    a, b = bench.dump_positions(10_000, 64, 7), bench.dump_positions(10_000, 64, 7)
+    assert np.array_equal(a, b) and a.size == 64 and np.all(np.diff(a) >= 0)
+    assert 0 <= a[0] and a[-1] < 10_000
+    assert not np.array_equal(a, bench.dump_positions(10_000, 64, 8))
+    x = np.arange(-50, 50, dtype=np.int16)
+    assert np.array_equal(bench.pcm_sample(x, 90, 100, 0), x[:90].astype(np.float32))
+    pos = bench.dump_positions(90, 10, 3)
+    assert np.array_equal(bench.pcm_sample(x, 90, 10, 3), x[pos].astype(np.float32))
+    sums = [0, -1, 0x0123456789ABCDEF, -(1 << 63)]
+    limbs = bench.checksum_limbs(sums)
+    assert limbs.dtype == np.float64 and limbs.shape == (4, 4)
+    back = [sum(int(v) << (16 * i) for i, v in enumerate(row)) for row in limbs]
+    assert back == [s & 0xFFFFFFFFFFFFFFFF for s in sums]
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) checks nothing against the oracle, and
+    --dump-outputs leaves every rank's PCM (each stream before its first
+    error) and per-stream checksums, equal to the oracle's here."""
+    import bench
+    import oracle
+    out = str(tmp_path / "dump")
+    rc, line, err = _bench(["--gpus", "2", "--streams", "5", "--eblocks", "120", "--steps", "2",
+                            "--warmup", "0", "--bad-stream", "3", "--dump-outputs", out],
+                           full=False)
+    assert rc == 0, err[-3000:]
+    assert line["bit_exact"] is None and line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["control_plane"]["checksums_match_oracle"] is None
+    assert line["control_plane"]["first_error_stream"] == 3
+    assert sorted(os.listdir(out)) == ["pcm.rank0.npy", "pcm.rank1.npy",
+                                       "pcm_checksum.rank0.npy", "pcm_checksum.rank1.npy"]
+    for rank, (lo, hi) in enumerate(line["control_plane"]["shards"]):
+        pcm = np.load(os.path.join(out, "pcm.rank%d.npy" % rank))
+        sums = np.load(os.path.join(out, "pcm_checksum.rank%d.npy" % rank))
+        assert pcm.dtype == np.float32 and sums.shape == (hi - lo, 4)
+        at = 0
+        for k, (i, bits, ch, eb, xa) in enumerate(bench.batch_inputs("C5", 5, 120, lo, hi, 3)):
+            ref, _, done, _ = oracle.decode(xa, eb, bits, ch)
+            ref = ref[:done * 32 * ch]
+            assert np.array_equal(pcm[at:at + ref.size], ref.astype(np.float32))
+            assert np.array_equal(sums[k], bench.checksum_limbs([bench.pcm_checksum_np(ref)])[0])
+            at += ref.size
+        assert at == pcm.size

@@ -13,10 +13,13 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 
 
-def _bench(args):
+def _bench(args, full=True):
+    """bench.py with --full (the oracle check, the roofline and the other
+    passes these tests assert on) unless `full` is False: a plain run."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py")] + args,
+    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py")] +
+                       (["--full"] if full else []) + args,
                        capture_output=True, text=True, env=env, timeout=240)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     return r.returncode, (json.loads(lines[-1]) if lines else None), r.stderr
@@ -54,7 +57,7 @@ def test_bench_c5_two_ranks_shared_gpu(built):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["BJXA_BENCH_BACKEND"] = "gloo-gpu"
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                        "--workload", "C5", "--streams", "20", "--eblocks", "3000",
+                        "--full", "--workload", "C5", "--streams", "20", "--eblocks", "3000",
                         "--steps", "3", "--warmup", "1", "--no-cpu", "--bad-stream", "13"],
                        capture_output=True, text=True, env=env, timeout=300)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -76,7 +79,7 @@ def test_bench_c5_three_ranks_shared_gpu(built):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["BJXA_BENCH_BACKEND"] = "gloo-gpu"
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "3",
-                        "--workload", "C5", "--streams", "17", "--eblocks", "2500",
+                        "--full", "--workload", "C5", "--streams", "17", "--eblocks", "2500",
                         "--steps", "2", "--warmup", "1", "--no-cpu", "--no-other"],
                        capture_output=True, text=True, env=env, timeout=300)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -161,3 +164,78 @@ def test_bench_other_config_child(built, name):
         assert line["first_error"] is None and 0 < line["spec_ms"] < line["ms_per_step"] * 2
     else:
         assert line["byte_exact"] is True
+
+
+def _limbs_to_int(row):
+    """a pcm_checksum.npy row (four 16-bit limbs, low first) as a signed int64"""
+    u = sum(int(v) << (16 * i) for i, v in enumerate(row))
+    return u - (1 << 64) if u >> 63 else u
+
+
+def test_bench_plain_line_and_dump_c3(built, tmp_path):
+    """A plain run (no --full) of the N = 1 headline: the timed steps and the
+    line's headline fields only, nothing checked or measured beside them;
+    --dump-outputs leaves the last timed step's PCM at the seeded positions,
+    which equal the oracle's over the prefix of the stream decoded here."""
+    import numpy as np
+    import bench
+    import oracle
+    from bjxa_amd import synth
+    out = str(tmp_path / "dump")
+    rc, line, err = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", out], full=False)
+    assert rc == 0, err[-2000:]
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 1
+    assert line["config"]["workload_id"] == "C3" and line["config"]["pipeline"] in (1, 2)
+    assert line["unit"] == "MSamples/s" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0
+    samples = line["config"]["samples_per_rank"]
+    assert line["value"] == pytest.approx(samples / line["ms_per_step"] / 1e3, rel=1e-3)
+    for k in ("bit_exact", "roofline", "cpu_baseline", "step_ms", "cold_single_decode"):
+        assert line[k] is None, k
+    assert "other_configs" not in line
+    assert sorted(os.listdir(out)) == ["pcm.npy", "pcm_checksum.npy", "status.npy"]
+    pcm = np.load(os.path.join(out, "pcm.npy"))
+    assert pcm.dtype == np.float32 and pcm.size == bench.DUMP_MAX_SAMPLES
+    status = np.load(os.path.join(out, "status.npy"))
+    assert status.dtype == np.float64 and status.shape == (3,)
+    assert status[0] == bench.NO_ERROR
+    assert np.load(os.path.join(out, "pcm_checksum.npy")).shape == (1, 4)
+    eb, bits, ch, _ = bench.WORKLOADS["C3"]
+    pre = 60_000
+    xa = synth.stream(eb, bits, ch, "A", seed=0)[:pre * ch * (bits * 4 + 1)]
+    ref, _, _, _ = oracle.decode(np.ascontiguousarray(xa), pre, bits, ch)
+    pos = bench.dump_positions(samples, bench.DUMP_MAX_SAMPLES, bench.DUMP_SEED)
+    m = int(np.searchsorted(pos, ref.size))
+    assert m > 50_000
+    assert np.array_equal(pcm[:m], ref[pos[:m]].astype(np.float32))
+
+
+def test_bench_plain_dump_c5_whole(built, tmp_path):
+    """--dump-outputs of a small C5-shaped job (every stream shorter than the
+    sample, so dumped whole) in a plain run: every stream's PCM before its
+    first error, its checksum and its first error equal the oracle's."""
+    import numpy as np
+    import bench
+    import oracle
+    out = str(tmp_path / "dump")
+    rc, line, err = _bench(["--gpus", "1", "--workload", "C5", "--streams", "5",
+                            "--eblocks", "700", "--steps", "2", "--warmup", "1",
+                            "--bad-stream", "3", "--dump-outputs", out], full=False)
+    assert rc == 0, err[-2000:]
+    assert line["full"] is False and line["bit_exact"] is None and line["roofline"] is None
+    assert line["control_plane"]["first_error_stream"] == 3 and line["ms_per_step"] > 0
+    pcm = np.load(os.path.join(out, "pcm.npy"))
+    sums = np.load(os.path.join(out, "pcm_checksum.npy"))
+    first = np.load(os.path.join(out, "first_error.npy"))
+    assert pcm.dtype == np.float32 and sums.dtype == first.dtype == np.float64
+    refs, at = [], 0
+    for i, bits, ch, eb, xa in bench.batch_inputs("C5", 5, 700, 0, 5, bad_stream=3):
+        ref, _, done, badc = oracle.decode(xa, eb, bits, ch)
+        ref = ref[:done * 32 * ch]
+        assert first[i] == (bench.NO_ERROR if done == eb else done * ch + badc)
+        assert _limbs_to_int(sums[i]) == bench.pcm_checksum_np(ref)
+        assert np.array_equal(pcm[at:at + ref.size], ref.astype(np.float32))
+        at += ref.size
+        refs.append(ref)
+    assert at == pcm.size and refs[3].size == 350 * 64

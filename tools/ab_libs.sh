@@ -14,7 +14,7 @@ for v in $VARIANTS; do
   export BJXA_LIB_PATH=$R/dbg/$v/libbjxa.so.0
   for w in $WL; do
     timeout -k 10 180 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/ab_${v}_${w}${MIX}_$r" -o run \
-        -- python3 "$R/bench.py" --no-cpu --no-other --steps 200 --workload $w --mix ${MIX:-A} \
+        -- python3 "$R/bench.py" --full --no-cpu --no-other --steps 200 --workload $w --mix ${MIX:-A} \
         > "$R/gpurun_out/ab_${v}_${w}${MIX}_$r.log" 2>&1
   done
 done

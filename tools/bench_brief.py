@@ -6,7 +6,7 @@ import sys
 
 def main(path):
     d = json.loads(open(path).read().strip().splitlines()[-1])
-    r = d.get("roofline", {})
+    r = d.get("roofline") or {}     # null in a plain (not --full) line
     print("%s n=%s value=%s ms/step=%s serial=%s spread=%s launch_ms=%s frac=%s step_frac=%s "
           "exact=%s" % (d["config"].get("workload_id", d["config"].get("workload")),
                         d["n_gpus"], d["value"], d["ms_per_step"], d.get("ms_per_step_serial"),

@@ -5,7 +5,8 @@
 # after a fault, a time limit or a crash):
 #   tests[=<pytest -k expr>]  pytest -m gpu (all, or the selected tests)
 #   smoke                     __graft_entry__.smoke()
-#   bench[=<args>]            python bench.py <args>, line -> <tag>_bench.json
+#   bench[=<args>]            python bench.py <args> (--full among them for the
+#                             whole line), line -> <tag>_bench.json
 #   ab=<wl>:<mix>[:<reps>[:<names>]]  tools/ab_inproc.py: this tree's library
 #                             against ab/<name>/libbjxa.so.0 for each name of the
 #                             comma list (default: every ab/*), interleaved in one

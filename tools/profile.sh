@@ -2,7 +2,7 @@
 # rocprofv3 evidence for the bench line (GPU box).  Output under
 # gpurun_out/prof_<tag>/:
 #   trace/    --kernel-trace --stats of the bench command itself (bench args
-#             as given; none = the driver's default `python bench.py`),
+#             after --full; none = the whole line, `python bench.py --full`),
 #             bench.json = the line that run printed
 #   pmc*/     one counter group per pass (counters never combined with trace
 #             domains), on a short run of the same workload
@@ -21,7 +21,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run \
-    -- python3 "$R/bench.py" "$@" > "$OUT/bench.json" 2> "$OUT/trace.log" || {
+    -- python3 "$R/bench.py" --full "$@" > "$OUT/bench.json" 2> "$OUT/trace.log" || {
 	echo "trace pass failed rc=$?"; exit 1; }
 PM="--steps 5 --warmup 1 --no-cpu --no-verify --no-other"
 i=0
