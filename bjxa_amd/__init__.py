@@ -62,6 +62,13 @@ class HipStream(ctypes.Structure):
                 ("state", ctypes.c_int16 * 4)]
 
 
+class EncStream(ctypes.Structure):
+    """bjxa_hip_enc_stream_t (include/bjxa_hip.h)."""
+    _fields_ = [("d_pcm", ctypes.c_void_p), ("d_xa", ctypes.c_void_p),
+                ("frames", ctypes.c_uint64), ("bits", ctypes.c_uint8),
+                ("channels", ctypes.c_uint8)]
+
+
 class HipTuning(ctypes.Structure):
     _fields_ = [("chunk", ctypes.c_uint32), ("warmup", ctypes.c_int32),
                 ("ev_spec", ctypes.c_void_p * 2), ("variant", ctypes.c_uint32)]
@@ -106,6 +113,11 @@ _SIGS = {
     "bjxa_hip_parse_headers_async": (ctypes.c_int, [_P, _SZ, ctypes.c_uint32, _P, _P]),
     # LIBBJXA_HIP_0.3
     "bjxa_hip_offload_threshold": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int64]),
+    # LIBBJXA_HIP_0.4
+    "bjxa_hip_enc_batch_new": (ctypes.c_void_p, [_P, ctypes.c_uint32, _P]),
+    "bjxa_hip_enc_batch_encode_async": (ctypes.c_int, [_P, _P]),
+    "bjxa_hip_enc_batch_free": (None, [_P]),
+    "bjxa_hip_encode_files": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_uint32]),
 }
 REFERENCE_SYMBOLS = {  # src/libbjxa.map:16-47
     "LIBBJXA_0.1": ["bjxa_decode", "bjxa_decode_format", "bjxa_decoder", "bjxa_dump_pcm",
@@ -121,7 +133,10 @@ EXTENSION_SYMBOLS = {"LIBBJXA_HIP_0.1": ["bjxa_hip_batch_decode_async", "bjxa_hi
                                          "bjxa_hip_decode_workspace", "bjxa_hip_encode_async",
                                          "bjxa_hip_version", "bjxa_hip_workspace_init"],
                      "LIBBJXA_HIP_0.2": ["bjxa_hip_parse_headers_async"],
-                     "LIBBJXA_HIP_0.3": ["bjxa_hip_offload_threshold"]}
+                     "LIBBJXA_HIP_0.3": ["bjxa_hip_offload_threshold"],
+                     "LIBBJXA_HIP_0.4": ["bjxa_hip_enc_batch_encode_async",
+                                         "bjxa_hip_enc_batch_free", "bjxa_hip_enc_batch_new",
+                                         "bjxa_hip_encode_files"]}
 
 
 def lib():
@@ -412,6 +427,79 @@ def parse_headers_device(d_src, stride, n, d_out, stream=0):
 def encode_device(d_pcm, frames, bits, channels, d_xa, stream=0):
     _check(lib().bjxa_hip_encode_async(d_pcm, frames, bits, channels, d_xa, stream),
            "bjxa_hip_encode_async")
+
+
+class EncodeBatch:
+    """bjxa_hip_enc_batch_*: many device-resident PCM streams encoded per
+    launch.
+
+    `streams` is a list of dicts with d_pcm, d_xa, frames, bits and
+    channels; `stream` here carries the upload of the batch's tables."""
+
+    def __init__(self, streams, stream=0):
+        arr = (EncStream * len(streams))()
+        for i, d in enumerate(streams):
+            arr[i] = EncStream(d["d_pcm"], d["d_xa"], d["frames"], d["bits"], d["channels"])
+        self.n = len(streams)
+        self._p = lib().bjxa_hip_enc_batch_new(arr, self.n, stream)
+        if not self._p:
+            e = ctypes.get_errno()
+            raise BjxaError(e, "bjxa_hip_enc_batch_new: %s" % os.strerror(e))
+
+    def encode(self, stream=0):
+        """Encode every stream: one kernel launch on `stream`, no host sync."""
+        _check(lib().bjxa_hip_enc_batch_encode_async(self._p, stream),
+               "bjxa_hip_enc_batch_encode_async")
+
+    def close(self):
+        if self._p:
+            lib().bjxa_hip_enc_batch_free(self._p)
+            self._p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def xa_file_size(wav, bits, clamp=False):
+    """Bytes of the XA file `bjxa encode --bits bits` makes of a WAV file
+    (32 + blocks * block_size_xa), from the raw RIFF fields; 0 where they
+    give no size (short file, channels or bits out of range).  `clamp`
+    bounds the announced PCM length by what the file holds."""
+    if len(wav) < 44 or bits not in (4, 6, 8):
+        return 0
+    ch, = struct.unpack("<H", bytes(wav[22:24]))
+    data_len, = struct.unpack("<I", bytes(wav[40:44]))
+    if ch not in (1, 2):
+        return 0
+    if clamp:
+        data_len = min(data_len, len(wav) - 44)
+    return 32 + (data_len // (2 * ch) + 31) // 32 * ch * (bits * 4 + 1)
+
+
+def encode_files(files, bits):
+    """bjxa_hip_encode_files: WAV files (bytes) -> [(XA file bytes, errno)].
+
+    `bits` is one int or one per file.  Every XA buffer is sized from its
+    WAV header; a refused file yields b"" and its errno."""
+    n = len(files)
+    bl = [bits] * n if isinstance(bits, int) else [int(b) for b in bits]
+    if len(bl) != n:
+        raise ValueError("encode_files: %d files, %d bits" % (n, len(bl)))
+    bufs = [ctypes.create_string_buffer(bytes(f), len(f)) for f in files]
+    # bounded by what the file can hold, whatever the header says
+    outs = [ctypes.create_string_buffer(max(32, xa_file_size(f, b, clamp=True)))
+            for f, b in zip(files, bl)]
+    wv = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in bufs])
+    wl = (ctypes.c_size_t * n)(*[len(f) for f in files])
+    ba = (ctypes.c_uint8 * n)(*[b & 0xFF for b in bl])
+    xa = (ctypes.c_void_p * n)(*[ctypes.addressof(o) for o in outs])
+    xl = (ctypes.c_size_t * n)(*[len(o) for o in outs])
+    st = (ctypes.c_int * n)()
+    _check(lib().bjxa_hip_encode_files(wv, wl, ba, xa, xl, st, n), "bjxa_hip_encode_files")
+    return [(o.raw if s == 0 else b"", int(s)) for o, s in zip(outs, st)]
 
 
 OFFLOAD_DECODE, OFFLOAD_ENCODE = 0, 1

@@ -779,3 +779,82 @@ bjxa_hip_decode_files(const void *const *xa, const size_t *xa_len,
 	free(which);
 	return (done);
 }
+
+/*
+ * bjxa_hip_encode_files (LIBBJXA_HIP_0.4): encode n complete WAV files (the
+ * 44-byte RIFF header of bjxa_parse_riff_header followed by the PCM) held in
+ * host memory into n complete XA files -- the 32-byte header of
+ * bjxa_dump_header followed by the blocks, what `bjxa encode --bits bits[i]`
+ * writes (src/bjxa_encode.c:62-106) -- with one batched GPU pass over all of
+ * them.  status[i] is 0 or the errno file i was refused with: EFAULT for a
+ * NULL buffer, EPROTO for a bad RIFF header or an empty stream, EINVAL for
+ * bits outside {4, 6, 8}, ENOBUFS for an input shorter than its header
+ * announces or an output smaller than 32 + blocks * block_size_xa; a
+ * refused file's output is not written.  Bytes past the PCM are ignored, as
+ * by the CLI.  Returns the number of files encoded, or -1 with errno
+ * (EFAULT, EINVAL, ENOMEM, or the device's ENODEV/ENOMEM/EIO) when the
+ * batch itself fails.
+ */
+int
+bjxa_hip_encode_files(const void *const *wav, const size_t *wav_len,
+    const uint8_t *bits, void *const *xa, const size_t *xa_len, int *status,
+    uint32_t n)
+{
+	struct bjxa__enc_job *jobs;
+	uint32_t nj = 0;
+	int done = 0;
+
+	NEED_PTR(wav);
+	NEED_PTR(wav_len);
+	NEED_PTR(bits);
+	NEED_PTR(xa);
+	NEED_PTR(xa_len);
+	NEED_PTR(status);
+	REQUIRE(n > 0, EINVAL);
+	jobs = calloc(n, sizeof *jobs);
+	if (jobs == NULL)
+		FAIL(ENOMEM);
+	for (uint32_t i = 0; i < n; i++) {
+		bjxa_encoder_t e;
+		bjxa_format_t f;
+
+		status[i] = 0;
+		if (wav[i] == NULL || xa[i] == NULL) {
+			status[i] = EFAULT;
+			continue;
+		}
+		if (wav_len[i] < BJXA_HEADER_SIZE_RIFF) {
+			status[i] = ENOBUFS;
+			continue;
+		}
+		memset(&e, 0, sizeof e);
+		e.magic = ENC_MAGIC;
+		if (bjxa_parse_riff_header(&f, wav[i], wav_len[i]) < 0 ||
+		    bjxa_encode_init(&e, &f, bits[i]) < 0) {
+			status[i] = errno;
+			continue;
+		}
+		if (wav_len[i] < BJXA_HEADER_SIZE_RIFF + (size_t)f.data_len_pcm ||
+		    xa_len[i] < BJXA_HEADER_SIZE_XA + (size_t)f.blocks *
+		    f.block_size_xa) {
+			status[i] = ENOBUFS;
+			continue;
+		}
+		(void)bjxa_dump_header(&e, xa[i], BJXA_HEADER_SIZE_XA);
+		jobs[nj].src = (const uint8_t *)wav[i] + BJXA_HEADER_SIZE_RIFF;
+		jobs[nj].dst = (uint8_t *)xa[i] + BJXA_HEADER_SIZE_XA;
+		jobs[nj].frames = e.samples;
+		jobs[nj].bits = e.bits;
+		jobs[nj].ch = e.channels;
+		nj++;
+	}
+	if (nj > 0 && bjxa__gpu_encode_many(jobs, nj) < 0) {
+		const int err = errno;
+		free(jobs);
+		FAIL(err);
+	}
+	for (uint32_t i = 0; i < n; i++)
+		done += status[i] == 0;
+	free(jobs);
+	return (done);
+}

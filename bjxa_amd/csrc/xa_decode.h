@@ -153,4 +153,29 @@ struct xa_enc_args {
 hipError_t xa_encode_launch(const xa_enc_args &a, unsigned bits, unsigned ch,
     hipStream_t st);
 
+/*
+ * Batched encode: many independent streams, mixed formats, one launch.  The
+ * grid is a flat space of waves; stream i owns the waves [first_wave,
+ * first_wave + ceil(ngroups_i / 64)), ngroups_i = ceil(eblocks * ch / 4),
+ * and wave w belongs to stream wstream[w] (the convention of
+ * xa_batch_args::wstream).
+ */
+struct xa_enc_batch_stream {		/* 64 B, device table entry */
+	const uint8_t *src;		/* PCM, 16-B aligned */
+	uint8_t *dst;			/* XA blocks, 4-B aligned */
+	uint64_t frames;
+	uint32_t eblocks;		/* ceil(frames / 32) */
+	uint32_t first_wave;
+	uint32_t fmt;			/* bits | channels << 8 */
+	uint32_t pad[7];
+};
+
+struct xa_enc_batch_args {
+	const xa_enc_batch_stream *streams;
+	const uint32_t *wstream;	/* stream of each wave */
+	uint32_t nstreams, nwaves;
+};
+
+hipError_t xa_encode_batch_launch(const xa_enc_batch_args &b, hipStream_t st);
+
 #endif

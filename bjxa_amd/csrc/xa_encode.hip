@@ -7,7 +7,9 @@
  * the top `bits` bits of every sample, zero-padding the last block.  There
  * is no state and no dependency between blocks, so this is pure streaming:
  * one lane packs one 4-block group (256 B of PCM -> 4*(bits*4+1) B of XA,
- * a whole number of dwords).
+ * a whole number of dwords).  xa_encode_waves encodes one stream per launch,
+ * xa_encode_batch any number of streams of mixed formats; both run the same
+ * wave body.
  */
 #include "xa_common.h"
 #include "xa_decode.h"
@@ -60,22 +62,30 @@ wave_sync()
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+#define XA_ENC_IN (64 * 256)	/* PCM bytes per wave */
+
+/*
+ * One wave's work: the 64 four-channel-block groups from grp0 of one stream
+ * (256 / CH eblocks, 16 KiB of PCM), staged and packed in the wave's own
+ * 16 KiB of LDS at `buf`.  Wave-level synchronization only, so the waves of
+ * a workgroup are free to work on different streams and formats
+ * (xa_encode_batch).  Every boundary is the stream's own: nothing is read
+ * past the 16-byte piece holding its last PCM byte, nothing written past
+ * eblocks * CH * BSZ bytes of its XA.
+ */
 template <int BITS, int CH>
-__global__ __launch_bounds__(64 * XA_ENC_WPB) void
-xa_encode_waves(xa_enc_args a)
+__device__ __forceinline__ void
+xa_encode_wave(const uint8_t *src, uint8_t *xa, const uint64_t frames,
+    const uint32_t eblocks, const uint64_t grp0, uint8_t *buf)
 {
 	constexpr int BSZ = BITS * 4 + 1, G = 4 / CH, GDW = BSZ;
-	constexpr int IN = 64 * 256;		/* PCM bytes per wave */
+	constexpr int IN = XA_ENC_IN;
 	constexpr int NOUT = 64 * GDW * 4;	/* XA bytes per wave */
-	__shared__ __attribute__((aligned(16))) uint8_t lds[XA_ENC_WPB * IN];
 	const int lane = threadIdx.x & 63;
-	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-	uint8_t *buf = lds + wv * IN;
-	const uint64_t grp0 = ((uint64_t)blockIdx.x * XA_ENC_WPB + wv) * 64u;
-	const uint64_t ngroups = ((uint64_t)a.eblocks + G - 1) / G;
+	const uint64_t ngroups = ((uint64_t)eblocks + G - 1) / G;
 	if (grp0 >= ngroups)
 		return;
-	const uint64_t pcm_bytes = a.frames * CH * 2u;
+	const uint64_t pcm_bytes = frames * CH * 2u;
 	const uint64_t base = grp0 * 256u;		/* wave's first PCM byte */
 	const bool full = base + IN <= pcm_bytes;
 
@@ -93,7 +103,7 @@ xa_encode_waves(xa_enc_args a)
 		uint64_t off = base + (uint64_t)row * 256u + piece * 16u;
 		if (!full && off > lastp)
 			off = lastp;	/* past the end: any valid piece */
-		__builtin_amdgcn_global_load_lds(a.src + off, LDS_PTR(buf + i * 1024),
+		__builtin_amdgcn_global_load_lds(src + off, LDS_PTR(buf + i * 1024),
 		    16, 0, 0);
 	}
 	__builtin_amdgcn_s_setprio(0);
@@ -133,9 +143,9 @@ xa_encode_waves(xa_enc_args a)
 	wave_sync();
 
 	/* the wave's XA run: groups past the last eblock are not written */
-	const uint64_t nxa = (uint64_t)a.eblocks * CH * BSZ;
+	const uint64_t nxa = (uint64_t)eblocks * CH * BSZ;
 	const uint64_t ostart = grp0 * 4u * BSZ;
-	uint8_t *dst = a.dst + ostart;
+	uint8_t *dst = xa + ostart;
 	const uint64_t valid = nxa - ostart < (uint64_t)NOUT ? nxa - ostart :
 	    (uint64_t)NOUT;
 	if (valid == (uint64_t)NOUT && ((uintptr_t)dst & 15u) == 0) {
@@ -159,6 +169,57 @@ xa_encode_waves(xa_enc_args a)
 				dst[4u * k + q] = (uint8_t)(v >> (8 * q));
 		}
 	}
+}
+
+template <int BITS, int CH>
+__global__ __launch_bounds__(64 * XA_ENC_WPB) void
+xa_encode_waves(xa_enc_args a)
+{
+	__shared__ __attribute__((aligned(16))) uint8_t lds[XA_ENC_WPB * XA_ENC_IN];
+	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	xa_encode_wave<BITS, CH>(a.src, a.dst, a.frames, a.eblocks,
+	    ((uint64_t)blockIdx.x * XA_ENC_WPB + wv) * 64u, lds + wv * XA_ENC_IN);
+}
+
+/*
+ * Batched encode: wave w of the flat grid belongs to stream wstream[w] and
+ * encodes that stream's groups 64 * (w - first_wave) .. +63.  The table
+ * reads are wave-uniform (scalar loads); the four waves of a workgroup may
+ * take four different cases of the switch.
+ */
+__global__ __launch_bounds__(64 * XA_ENC_WPB) void
+xa_encode_batch(xa_enc_batch_args b)
+{
+	__shared__ __attribute__((aligned(16))) uint8_t lds[XA_ENC_WPB * XA_ENC_IN];
+	const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const uint32_t w = blockIdx.x * XA_ENC_WPB + wv;
+	if (w >= b.nwaves)
+		return;
+	const xa_enc_batch_stream *s = b.streams +
+	    __builtin_amdgcn_readfirstlane(b.wstream[w]);
+	const uint8_t *src = s->src;
+	uint8_t *dst = s->dst;
+	const uint64_t frames = s->frames;
+	const uint32_t eblocks = s->eblocks;
+	const uint64_t grp0 = (uint64_t)(w - s->first_wave) * 64u;
+	uint8_t *buf = lds + wv * XA_ENC_IN;
+#define E(B, C) case (B) | (C) << 8: \
+	xa_encode_wave<B, C>(src, dst, frames, eblocks, grp0, buf); break
+	switch (__builtin_amdgcn_readfirstlane(s->fmt)) {
+	E(4, 1); E(6, 1); E(8, 1); E(4, 2); E(6, 2); E(8, 2);
+	}
+#undef E
+}
+
+hipError_t
+xa_encode_batch_launch(const xa_enc_batch_args &b, hipStream_t st)
+{
+	const unsigned grid = (b.nwaves + XA_ENC_WPB - 1) / XA_ENC_WPB;
+	if (grid == 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(xa_encode_batch, dim3(grid), dim3(64 * XA_ENC_WPB), 0,
+	    st, b);
+	return hipGetLastError();
 }
 
 hipError_t

@@ -1,6 +1,7 @@
 /*
  * xa_files.hip -- many host streams in one batched GPU pass
- * (bjxa_hip_decode_files -> bjxa__gpu_decode_many).
+ * (bjxa_hip_decode_files -> bjxa__gpu_decode_many, bjxa_hip_encode_files ->
+ * bjxa__gpu_encode_many).
  *
  * Host side of the file-level batch: the callers'
  * XA block data is gathered into the device input image and the decoded PCM
@@ -68,6 +69,8 @@ struct files_ctx {
 	size_t in_cap = 0, out_cap = 0, st_cap = 0;
 	void *d_bws = NULL;			/* batch workspace, kept */
 	size_t bws_cap = 0;
+	void *d_etab = NULL;			/* encode batch tables, kept */
+	size_t etab_cap = 0;
 	copy_pool *pool = NULL;
 };
 
@@ -232,6 +235,126 @@ bjxa__gpu_decode_many(struct bjxa__job *jobs, uint32_t n)
 		}
 		olen[i] = bytes;
 	}
+	/* out: slab k+1 downloads while slab k scatters */
+	{
+		const size_t nslab = (out_total + SLAB - 1) / SLAB;
+		auto fetch = [&](size_t k) {
+			const size_t lo = k * SLAB, hi = std::min(out_total,
+			    lo + SLAB);
+			return hipMemcpyAsync(c.h_slab[k & 1], c.d_out + lo,
+			    hi - lo, hipMemcpyDeviceToHost, c.stream) ==
+			    hipSuccess && hipEventRecord(c.ev[k & 1],
+			    c.stream) == hipSuccess;
+		};
+		if (nslab > 0 && !fetch(0))
+			goto io;
+		for (size_t k = 0; k < nslab; k++) {
+			if (k + 1 < nslab && !fetch(k + 1))
+				goto io;
+			if (hipEventSynchronize(c.ev[k & 1]) != hipSuccess)
+				goto io;
+			const size_t lo = k * SLAB, hi = std::min(out_total,
+			    lo + SLAB);
+			slab_pieces(pcs, c.h_slab[k & 1], lo, hi, ooff, olen,
+			    odst, false);
+			c.pool->run(pcs);
+		}
+	}
+	TMARK("d2h");
+	return 0;
+io:
+	(void)hipStreamSynchronize(c.stream);
+	errno = EIO;
+	return -1;
+}
+
+/*
+ * The same pipeline the other way (bjxa_hip_encode_files): the callers' PCM
+ * is gathered into the input image, one xa_encode_batch launch encodes every
+ * stream, and the XA image is scattered into the callers' buffers.  Both
+ * images place a stream at a 16-byte aligned offset: the kernel needs that
+ * of its PCM, and full waves of aligned XA take its 16-byte stores.  The
+ * slack between two streams is never gathered or scattered; the kernel
+ * masks what it stages past a stream's last frame.
+ */
+extern "C" int
+bjxa__gpu_encode_many(struct bjxa__enc_job *jobs, uint32_t n)
+{
+	files_ctx &c = ctx;
+	std::lock_guard<std::mutex> guard(c.m);
+#ifdef XA_FILES_TIMING
+	const double t0 = now_ms();
+#endif
+	if (!bjxa__gpu_present()) {
+		errno = ENODEV;
+		return -1;
+	}
+	if (setup(c) < 0) {
+		errno = EIO;
+		return -1;
+	}
+	std::vector<size_t> ioff(n), ilen(n), ooff(n), olen(n);
+	std::vector<uint8_t *> isrc(n), odst(n);
+	size_t in_total = 0, out_total = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		const size_t eb = (size_t)((jobs[i].frames + 31) / 32);
+		ilen[i] = (size_t)jobs[i].frames * jobs[i].ch * 2u;
+		ioff[i] = in_total;
+		in_total += (ilen[i] + 15) & ~(size_t)15;
+		isrc[i] = (uint8_t *)jobs[i].src;
+		olen[i] = eb * jobs[i].ch * (jobs[i].bits * 4 + 1);
+		ooff[i] = out_total;
+		out_total += (olen[i] + 15) & ~(size_t)15;
+		odst[i] = (uint8_t *)jobs[i].dst;
+	}
+	if (grow_dev(&c.d_in, &c.in_cap, in_total + 16) < 0 ||
+	    grow_dev(&c.d_out, &c.out_cap, out_total + 16) < 0) {
+		errno = ENOMEM;
+		return -1;
+	}
+	std::vector<bjxa_hip_enc_stream_t> hs(n);
+	for (uint32_t i = 0; i < n; i++) {
+		memset(&hs[i], 0, sizeof hs[i]);
+		hs[i].d_pcm = c.d_in + ioff[i];
+		hs[i].d_xa = c.d_out + ooff[i];
+		hs[i].frames = jobs[i].frames;
+		hs[i].bits = jobs[i].bits;
+		hs[i].channels = jobs[i].ch;
+	}
+	TMARK("setup");
+
+	/* in: gather slab k while slab k-1 uploads */
+	std::vector<piece> pcs;
+	bool used[2] = { false, false };
+	for (size_t lo = 0, k = 0; lo < in_total; lo += SLAB, k++) {
+		const size_t hi = std::min(in_total, lo + SLAB);
+		uint8_t *slab = c.h_slab[k & 1];
+		if (used[k & 1] && hipEventSynchronize(c.ev[k & 1]) !=
+		    hipSuccess)
+			goto io;
+		slab_pieces(pcs, slab, lo, hi, ioff, ilen, isrc, true);
+		c.pool->run(pcs);
+		if (hipMemcpyAsync(c.d_in + lo, slab, hi - lo,
+		    hipMemcpyHostToDevice, c.stream) != hipSuccess ||
+		    hipEventRecord(c.ev[k & 1], c.stream) != hipSuccess)
+			goto io;
+		used[k & 1] = true;
+	}
+	TMARK("h2d");
+	{
+		bjxa_hip_enc_batch_t *b = bjxa__enc_batch_new(hs.data(), n,
+		    c.stream, &c.d_etab, &c.etab_cap);
+		if (b == NULL)
+			return -1;
+		const int r = bjxa_hip_enc_batch_encode_async(b, c.stream);
+		const int e = errno;
+		bjxa_hip_enc_batch_free(b);	/* waits for the kernel */
+		if (r < 0) {
+			errno = e;
+			return -1;
+		}
+	}
+	TMARK("encode");
 	/* out: slab k+1 downloads while slab k scatters */
 	{
 		const size_t nslab = (out_total + SLAB - 1) / SLAB;

@@ -62,6 +62,27 @@ bjxa_hip_batch_t *bjxa__batch_new(const bjxa_hip_stream_t *s, uint32_t n,
 int bjxa__gpu_encode(struct bjxa__gpu *g, const void *src, uint64_t frames,
     unsigned bits, unsigned ch, void *dst);
 
+/* one stream of a many-file encode (bjxa_hip_encode_files) */
+struct bjxa__enc_job {
+	const void	*src;		/* host PCM, frames * ch * 2 bytes */
+	void		*dst;		/* host XA blocks destination */
+	uint64_t	frames;
+	uint8_t		bits, ch;
+};
+
+/*
+ * Encode n independent streams from host memory in one batched pass
+ * (bjxa_hip_enc_batch_*); each job's ceil(frames/32) eblocks land in its
+ * dst.  Returns 0 or -1/errno (ENODEV, ENOMEM, EIO).
+ */
+int bjxa__gpu_encode_many(struct bjxa__enc_job *jobs, uint32_t n);
+
+/* bjxa_hip_enc_batch_new with its tables in a device buffer the caller
+ * keeps across batches (grown in place; not freed by
+ * bjxa_hip_enc_batch_free) */
+bjxa_hip_enc_batch_t *bjxa__enc_batch_new(const bjxa_hip_enc_stream_t *s,
+    uint32_t n, void *stream, void **tab_cache, size_t *tab_cap);
+
 /*
  * CPU core (xa_cpu.c): the same contracts as bjxa__gpu_decode and
  * bjxa__gpu_encode, on the calling thread; they cannot fail.

@@ -816,6 +816,166 @@ bjxa_hip_batch_free(bjxa_hip_batch_t *b)
 	free(b);
 }
 
+/* ------------------------------------------------------------------ */
+/* batched encode (bjxa_hip_enc_batch_*)                                */
+
+struct bjxa_hip_enc_batch {
+	void		*d_tab;		/* stream records, then wstream[] */
+	bool		owns_tab;	/* false: a table buffer lent by the caller */
+	bool		launched;	/* `done` has been recorded */
+	hipEvent_t	done;		/* after the last encode's kernel */
+	xa_enc_batch_args args;
+};
+
+static int
+enc_stream_ok(const bjxa_hip_enc_stream_t *s)
+{
+	return s->d_pcm != NULL && s->d_xa != NULL && s->frames != 0 &&
+	    (s->bits == 4 || s->bits == 6 || s->bits == 8) &&
+	    (s->channels == 1 || s->channels == 2) &&
+	    (s->frames + 31) / 32 <= 0xffffffffu &&
+	    ((uintptr_t)s->d_pcm & 15u) == 0 && ((uintptr_t)s->d_xa & 3u) == 0;
+}
+
+extern "C" bjxa_hip_enc_batch_t *
+bjxa_hip_enc_batch_new(const bjxa_hip_enc_stream_t *s, uint32_t n, void *stream)
+{
+	return bjxa__enc_batch_new(s, n, stream, NULL, NULL);
+}
+
+/*
+ * bjxa_hip_enc_batch_new, optionally with its tables in a device buffer the
+ * caller keeps across batches (as bjxa__batch_new's workspace).
+ */
+extern "C" bjxa_hip_enc_batch_t *
+bjxa__enc_batch_new(const bjxa_hip_enc_stream_t *s, uint32_t n, void *stream,
+    void **tab_cache, size_t *tab_cap)
+{
+	if (s == NULL || n == 0) {
+		errno = EINVAL;
+		return NULL;
+	}
+	/* a stream's waves: 64 groups of 4 channel blocks each */
+	uint64_t nwaves = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		if (!enc_stream_ok(&s[i])) {
+			errno = EINVAL;
+			return NULL;
+		}
+		const uint64_t cblocks = (s[i].frames + 31) / 32 * s[i].channels;
+		nwaves += (cblocks + 255) / 256;
+	}
+	/* the grid: ceil(nwaves / 4) workgroups, and 32-bit wave indices */
+	if (nwaves > 0x7fffffffu) {
+		errno = EINVAL;
+		return NULL;
+	}
+	if (!bjxa__gpu_present()) {
+		errno = ENODEV;
+		return NULL;
+	}
+	const size_t o_wav = al64((size_t)n * sizeof(xa_enc_batch_stream));
+	const size_t len = o_wav + al64(nwaves * 4);
+	uint8_t *h = (uint8_t *)calloc(1, len);
+	bjxa_hip_enc_batch_t *b = (bjxa_hip_enc_batch_t *)calloc(1, sizeof *b);
+	if (h == NULL || b == NULL) {
+		free(h);
+		free(b);
+		errno = ENOMEM;
+		return NULL;
+	}
+	xa_enc_batch_stream *hs = (xa_enc_batch_stream *)h;
+	uint32_t *hw = (uint32_t *)(h + o_wav);
+	for (uint32_t i = 0, wv = 0; i < n; i++) {
+		const uint64_t eb = (s[i].frames + 31) / 32;
+		const uint32_t k = (uint32_t)((eb * s[i].channels + 255) / 256);
+		hs[i].src = (const uint8_t *)s[i].d_pcm;
+		hs[i].dst = (uint8_t *)s[i].d_xa;
+		hs[i].frames = s[i].frames;
+		hs[i].eblocks = (uint32_t)eb;
+		hs[i].first_wave = wv;
+		hs[i].fmt = s[i].bits | (uint32_t)s[i].channels << 8;
+		for (uint32_t j = 0; j < k; j++)
+			hw[wv++] = i;
+	}
+	uint8_t *tab = NULL;
+	if (tab_cache != NULL && *tab_cap >= len) {
+		tab = (uint8_t *)*tab_cache;
+	} else {
+		if (tab_cache != NULL) {
+			/* the previous user of the cache has completed */
+			(void)hipStreamSynchronize((hipStream_t)stream);
+			(void)hipFree(*tab_cache);
+			*tab_cache = NULL;
+			*tab_cap = 0;
+		}
+		if (hipMalloc((void **)&tab, len) != hipSuccess) {
+			free(h);
+			free(b);
+			errno = ENOMEM;
+			return NULL;
+		}
+		if (tab_cache != NULL) {
+			*tab_cache = tab;
+			*tab_cap = len;
+		}
+	}
+	b->d_tab = tab;
+	b->owns_tab = tab_cache == NULL;
+	b->args.streams = (const xa_enc_batch_stream *)tab;
+	b->args.wstream = (const uint32_t *)(tab + o_wav);
+	b->args.nstreams = n;
+	b->args.nwaves = (uint32_t)nwaves;
+	/* stream-ordered upload: a lent table may still be in use by an
+	 * earlier batch on the same stream (the files path) */
+	const bool bad = hipEventCreateWithFlags(&b->done,
+	    hipEventDisableTiming) != hipSuccess;
+	if (bad || hipMemcpyAsync(tab, h, len, hipMemcpyHostToDevice,
+	    (hipStream_t)stream) != hipSuccess ||
+	    hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
+		if (!bad)
+			(void)hipEventDestroy(b->done);
+		if (b->owns_tab)
+			(void)hipFree(tab);
+		free(h);
+		free(b);
+		errno = EIO;
+		return NULL;
+	}
+	free(h);
+	return b;
+}
+
+extern "C" int
+bjxa_hip_enc_batch_encode_async(bjxa_hip_enc_batch_t *b, void *stream)
+{
+	if (b == NULL) {
+		errno = EINVAL;
+		return -1;
+	}
+	if (xa_encode_batch_launch(b->args, (hipStream_t)stream) != hipSuccess ||
+	    hipEventRecord(b->done, (hipStream_t)stream) != hipSuccess) {
+		errno = EIO;
+		return -1;
+	}
+	b->launched = true;
+	return 0;
+}
+
+/* waits for the batch's own last encode only (not the whole device) */
+extern "C" void
+bjxa_hip_enc_batch_free(bjxa_hip_enc_batch_t *b)
+{
+	if (b == NULL)
+		return;
+	if (b->launched)
+		(void)hipEventSynchronize(b->done);
+	(void)hipEventDestroy(b->done);
+	if (b->owns_tab)
+		(void)hipFree(b->d_tab);
+	free(b);
+}
+
 extern "C" const char *
 bjxa_hip_version(void)
 {

@@ -50,6 +50,14 @@ bjxa__gpu_decode_many(struct bjxa__job *jobs, uint32_t n)
 }
 
 int
+bjxa__gpu_encode_many(struct bjxa__enc_job *jobs, uint32_t n)
+{
+	(void)jobs, (void)n;
+	errno = ENODEV;
+	return -1;
+}
+
+int
 bjxa__gpu_encode(struct bjxa__gpu *g, const void *src, uint64_t frames,
     unsigned bits, unsigned ch, void *dst)
 {

@@ -165,6 +165,52 @@ int bjxa_hip_parse_headers_async(const void *d_src, size_t stride, uint32_t n,
 #define BJXA_HIP_OFFLOAD_ENCODE	1
 int64_t bjxa_hip_offload_threshold(int direction, int64_t eblocks);
 
+/*
+ * Batched encode (LIBBJXA_HIP_0.4): n independent device-resident PCM
+ * streams (any mix of bits and channels) in one kernel launch.
+ * bjxa_hip_enc_batch_new validates every descriptor (EINVAL: n == 0, a NULL
+ * pointer, frames == 0, bad bits or channels, misalignment, more than
+ * 2^32 - 1 eblocks, more waves in total than one grid holds) before it needs
+ * the device (ENODEV), then builds and uploads the batch's tables (ENOMEM,
+ * EIO).  The descriptors, including the device buffers they name, are
+ * captured: re-create the batch for other buffers.  Stream i's XA is written
+ * to exactly ceil(frames/32) * channels * (bits*4 + 1) bytes at d_xa and
+ * its PCM read no further than the 16-byte piece holding its last sample,
+ * so streams may be packed into one allocation.  `stream` of _new is used
+ * for the upload and synchronized.  bjxa_hip_enc_batch_encode_async is one
+ * launch on `stream`, no host sync, repeatable; _free waits for the batch's
+ * own last encode only.
+ */
+typedef struct {
+	const void	*d_pcm;		/* 16-bit PCM, channels interleaved, 16-B aligned */
+	void		*d_xa;		/* XA blocks out (no header), 4-B aligned */
+	uint64_t	frames;		/* > 0; ceil(frames/32) eblocks are written */
+	uint8_t		bits;		/* 4, 6 or 8 */
+	uint8_t		channels;	/* 1 or 2 */
+} bjxa_hip_enc_stream_t;
+
+typedef struct bjxa_hip_enc_batch bjxa_hip_enc_batch_t;
+bjxa_hip_enc_batch_t *bjxa_hip_enc_batch_new(const bjxa_hip_enc_stream_t *s,
+    uint32_t n, void *stream);
+int bjxa_hip_enc_batch_encode_async(bjxa_hip_enc_batch_t *b, void *stream);
+void bjxa_hip_enc_batch_free(bjxa_hip_enc_batch_t *b);
+
+/*
+ * Encode n complete WAV files (44-byte RIFF header + 16-bit PCM) held in
+ * host memory into n complete XA files (32-byte header + blocks), each
+ * byte-identical to `bjxa encode --bits bits[i]` of file i, with one batched
+ * GPU pass (LIBBJXA_HIP_0.4).  xa[i] needs 32 + blocks * block_size_xa
+ * bytes; bytes of wav[i] past 44 + data_len_pcm are ignored.  status[i]: 0,
+ * EFAULT (NULL wav[i] or xa[i]), EPROTO (bad RIFF header, empty stream),
+ * EINVAL (bits not 4, 6 or 8) or ENOBUFS (input shorter than its header
+ * announces, output too small); a refused file leaves xa[i] untouched and
+ * needs no device.  Returns the number of files encoded, or -1 with errno
+ * (EINVAL, EFAULT, ENOMEM, ENODEV, EIO) if the batch itself fails.
+ */
+int bjxa_hip_encode_files(const void *const *wav, const size_t *wav_len,
+    const uint8_t *bits, void *const *xa, const size_t *xa_len,
+    int *status, uint32_t n);
+
 /* library/kernels build identifier, e.g. "bjxa-mi355x gfx950 ..." */
 const char *bjxa_hip_version(void);
 
