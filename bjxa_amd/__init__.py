@@ -118,6 +118,11 @@ _SIGS = {
     "bjxa_hip_enc_batch_encode_async": (ctypes.c_int, [_P, _P]),
     "bjxa_hip_enc_batch_free": (None, [_P]),
     "bjxa_hip_encode_files": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_uint32]),
+    # LIBBJXA_HIP_0.5
+    "bjxa_hip_encode_adaptive_async": (ctypes.c_int, [_P, ctypes.c_uint64, ctypes.c_uint,
+                                                      ctypes.c_uint, ctypes.c_uint32, _P, _P]),
+    "bjxa_hip_encode_adaptive": (ctypes.c_int, [_P, ctypes.c_uint64, ctypes.c_uint,
+                                                ctypes.c_uint, ctypes.c_uint32, _P]),
 }
 REFERENCE_SYMBOLS = {  # src/libbjxa.map:16-47
     "LIBBJXA_0.1": ["bjxa_decode", "bjxa_decode_format", "bjxa_decoder", "bjxa_dump_pcm",
@@ -136,7 +141,9 @@ EXTENSION_SYMBOLS = {"LIBBJXA_HIP_0.1": ["bjxa_hip_batch_decode_async", "bjxa_hi
                      "LIBBJXA_HIP_0.3": ["bjxa_hip_offload_threshold"],
                      "LIBBJXA_HIP_0.4": ["bjxa_hip_enc_batch_encode_async",
                                          "bjxa_hip_enc_batch_free", "bjxa_hip_enc_batch_new",
-                                         "bjxa_hip_encode_files"]}
+                                         "bjxa_hip_encode_files"],
+                     "LIBBJXA_HIP_0.5": ["bjxa_hip_encode_adaptive",
+                                         "bjxa_hip_encode_adaptive_async"]}
 
 
 def lib():
@@ -502,7 +509,48 @@ def encode_files(files, bits):
     return [(o.raw if s == 0 else b"", int(s)) for o, s in zip(outs, st)]
 
 
-OFFLOAD_DECODE, OFFLOAD_ENCODE = 0, 1
+ADAPTIVE_SYNC_DEFAULT = 64
+
+
+def encode_adaptive_device(d_pcm, frames, bits, channels, d_xa, sync=ADAPTIVE_SYNC_DEFAULT,
+                           stream=0):
+    """bjxa_hip_encode_adaptive_async: one launch on `stream`, no host sync."""
+    _check(lib().bjxa_hip_encode_adaptive_async(d_pcm, frames, bits, channels, sync, d_xa,
+                                                stream), "bjxa_hip_encode_adaptive_async")
+
+
+def encode_adaptive(pcm, frames, bits, channels, sync=ADAPTIVE_SYNC_DEFAULT):
+    """bjxa_hip_encode_adaptive: int16 PCM (host) -> XA blocks (uint8 array),
+    the best predictor and range per channel block, prediction restarting
+    every `sync` blocks."""
+    import numpy as np
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    if frames > 0 and pcm.size < frames * channels:
+        raise ValueError("encode_adaptive: %d samples for %d frames" % (pcm.size, frames))
+    n = (frames + 31) // 32 * channels * (bits * 4 + 1) if bits in (4, 6, 8) else 0
+    out = np.empty(max(n, 1), dtype=np.uint8)
+    _check(lib().bjxa_hip_encode_adaptive(pcm.ctypes.data, frames, bits, channels, sync,
+                                          out.ctypes.data), "bjxa_hip_encode_adaptive")
+    return out[:n]
+
+
+def encode_wav_adaptive(data, bits=6, sync=ADAPTIVE_SYNC_DEFAULT):
+    """WAV bytes -> XA file bytes, as `bjxa encode --adaptive --bits bits`."""
+    import numpy as np
+    fmt = parse_riff_header(data[:44])
+    e = Encoder()
+    try:
+        fmt = e.init(fmt, bits)
+        hdr = e.dump_header()
+    finally:
+        e.close()
+    ch = fmt["channels"]
+    frames = fmt["data_len_pcm"] // (2 * ch)
+    pcm = np.frombuffer(data, dtype="<i2", offset=44, count=frames * ch).astype(np.int16)
+    return hdr + encode_adaptive(pcm, frames, bits, ch, sync).tobytes()
+
+
+OFFLOAD_DECODE, OFFLOAD_ENCODE, OFFLOAD_ENCODE_ADAPTIVE = 0, 1, 2
 
 
 def offload_threshold(direction, eblocks=-1):

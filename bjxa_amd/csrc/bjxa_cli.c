@@ -8,7 +8,10 @@
  *
  *   bjxa help
  *   bjxa decode [<xa file> [<wav file>]]
- *   bjxa encode [--bits <4|6|8>] [<wav file> [<xa file>]]
+ *   bjxa encode [--bits <4|6|8>] [--adaptive] [<wav file> [<xa file>]]
+ *
+ * --adaptive is this build's own (bjxa_hip_encode_adaptive, DESIGN.md §3
+ * "Adaptive encode").
  *
  * A missing file operand or "-" is standard input/output.  Failures print
  * "bjxa: <reason>" plus the usage for command-line errors, "Error: ..." for
@@ -34,6 +37,7 @@
 #include <sys/types.h>
 
 #include "bjxa.h"		/* expects <stdio.h> and ssize_t, as the reference's */
+#include "bjxa_hip.h"		/* --adaptive */
 
 static const char *prog = "bjxa";
 
@@ -51,9 +55,11 @@ usage(FILE *f)
 	    "  decode [<xa file> [<wav file>]]\n"
 	    "    Convert an XA file into a WAV file.\n"
 	    "\n"
-	    "  encode [--bits <4|6|8>] [<wav file> [<xa file>]]\n"
+	    "  encode [--bits <4|6|8>] [--adaptive] [<wav file> [<xa file>]]\n"
 	    "    Convert a WAV file into an XA file, with 6 bits per sample\n"
-	    "    unless --bits says otherwise.\n"
+	    "    unless --bits says otherwise.  With --adaptive the encoder\n"
+	    "    picks the best predictor and range of every block; without\n"
+	    "    it, it writes what the reference encoder writes.\n"
 	    "\n"
 	    "A missing file name, or \"-\", means standard input or output.\n",
 	    prog);
@@ -276,6 +282,41 @@ done:
 	return (rc);
 }
 
+/* --adaptive: the whole stream through bjxa_hip_encode_adaptive; a short
+ * read behaves as in encode_stream */
+static int
+encode_adaptive(const bjxa_format_t *fmt, FILE *in, FILE *out)
+{
+	const size_t xa_len = (size_t)fmt->block_size_xa * fmt->blocks;
+	void *xa = malloc(xa_len + 1), *pcm = malloc((size_t)fmt->data_len_pcm + 1);
+	const unsigned bits = (fmt->block_size_xa / fmt->channels - 1u) / 4u;
+	size_t got;
+	uint32_t n;
+	int rc = -1;
+
+	if (xa == NULL || pcm == NULL) {
+		perror("malloc");
+		goto done;
+	}
+	got = fread(pcm, 1, fmt->data_len_pcm, in);
+	n = got == fmt->data_len_pcm ? fmt->blocks :
+	    (uint32_t)(got / fmt->block_size_pcm);
+	if (n > 0 && bjxa_hip_encode_adaptive(pcm, got == fmt->data_len_pcm ?
+	    got / (2u * fmt->channels) : (uint64_t)n * 32u, bits, fmt->channels,
+	    BJXA_HIP_ADAPTIVE_SYNC_DEFAULT, xa) < 0)
+		perror("bjxa_hip_encode_adaptive");
+	else if (n > 0 && fwrite(xa, (size_t)n * fmt->block_size_xa, 1, out) != 1)
+		perror("fwrite");
+	else if (n < fmt->blocks)
+		read_error(in);
+	else
+		rc = 0;
+done:
+	free(xa);
+	free(pcm);
+	return (rc);
+}
+
 static int
 encode_blocks(bjxa_encoder_t *enc, const bjxa_format_t *fmt, FILE *in,
     FILE *out)
@@ -309,7 +350,7 @@ encode_blocks(bjxa_encoder_t *enc, const bjxa_format_t *fmt, FILE *in,
 }
 
 static int
-cmd_encode(FILE *in, FILE *out, unsigned bits)
+cmd_encode(FILE *in, FILE *out, unsigned bits, int adaptive)
 {
 	bjxa_encoder_t *enc = bjxa_encoder();
 	bjxa_format_t fmt;
@@ -327,6 +368,8 @@ cmd_encode(FILE *in, FILE *out, unsigned bits)
 		perror("bjxa_encode_format");
 	else if (bjxa_fwrite_header(enc, out) < 0)
 		perror("bjxa_fwrite_header");
+	else if (adaptive)
+		rc = encode_adaptive(&fmt, in, out);
 	else
 		rc = block_calls() ? encode_blocks(enc, &fmt, in, out) :
 		    encode_stream(enc, &fmt, in, out);
@@ -361,20 +404,34 @@ main(int argc, char **argv)
 	}
 	if (strcmp(action, "encode") == 0) {
 		unsigned bits = 6;
-		if (argc > 0 && strcmp(argv[0], "--bits") == 0) {
-			if (argc < 2)
-				bad_usage("Missing number of bits per sample");
-			const char *v = argv[1];
-			if (strcmp(v, "4") != 0 && strcmp(v, "6") != 0 &&
-			    strcmp(v, "8") != 0)
-				bad_usage("Invalid number of bits per sample");
-			bits = (unsigned)(v[0] - '0');
-			argc -= 2;
-			argv += 2;
+		int adaptive = 0, have_bits = 0;
+		/* each option once, in either order */
+		for (;;) {
+			if (argc > 0 && !have_bits &&
+			    strcmp(argv[0], "--bits") == 0) {
+				if (argc < 2)
+					bad_usage("Missing number of bits per sample");
+				const char *v = argv[1];
+				if (strcmp(v, "4") != 0 && strcmp(v, "6") != 0 &&
+				    strcmp(v, "8") != 0)
+					bad_usage("Invalid number of bits per sample");
+				bits = (unsigned)(v[0] - '0');
+				have_bits = 1;
+				argc -= 2;
+				argv += 2;
+			} else if (argc > 0 && !adaptive &&
+			    strcmp(argv[0], "--adaptive") == 0) {
+				adaptive = 1;
+				argc--;
+				argv++;
+			} else {
+				break;
+			}
 		}
 		if (argc > 2)
 			bad_usage("Too many arguments");
-		if (redirect(argc, argv) < 0 || cmd_encode(stdin, stdout, bits) < 0)
+		if (redirect(argc, argv) < 0 ||
+		    cmd_encode(stdin, stdout, bits, adaptive) < 0)
 			return (EXIT_FAILURE);
 		return (EXIT_SUCCESS);
 	}

@@ -116,8 +116,13 @@ read_all(void *buf, size_t n, FILE *file)
  */
 #define OFFLOAD_DECODE_DEFAULT	1024u
 #define OFFLOAD_ENCODE_DEFAULT	4096u
+/* bjxa_hip_encode_adaptive, whole streams: the routes cross at 4 (stereo)
+ * to 8 (mono) eblocks (DESIGN.md §3 "Adaptive encode",
+ * profiles/encode_adaptive.json) */
+#define OFFLOAD_ADAPTIVE_DEFAULT	8u
+#define OFFLOAD_DIRS		3
 
-static uint64_t offload_min[2];
+static uint64_t offload_min[OFFLOAD_DIRS];
 #ifdef BJXA_TEST_HOOKS
 static int fault_gpu_decode;	/* BJXA_TEST_FAULT=gpu-decode */
 #endif
@@ -143,13 +148,13 @@ parse_threshold(const char *v, uint64_t *out)
 static void
 offload_init(void)
 {
-	static const char *const env[2] = { "BJXA_OFFLOAD_DECODE",
-	    "BJXA_OFFLOAD_ENCODE" };
-	const uint64_t dflt[2] = { OFFLOAD_DECODE_DEFAULT,
-	    OFFLOAD_ENCODE_DEFAULT };
+	static const char *const env[OFFLOAD_DIRS] = { "BJXA_OFFLOAD_DECODE",
+	    "BJXA_OFFLOAD_ENCODE", "BJXA_OFFLOAD_ENCODE_ADAPTIVE" };
+	const uint64_t dflt[OFFLOAD_DIRS] = { OFFLOAD_DECODE_DEFAULT,
+	    OFFLOAD_ENCODE_DEFAULT, OFFLOAD_ADAPTIVE_DEFAULT };
 	const int saved = errno;
 
-	for (int d = 0; d < 2; d++) {
+	for (int d = 0; d < OFFLOAD_DIRS; d++) {
 		const char *v = getenv(env[d]);
 		uint64_t n = dflt[d];
 		if (v != NULL && *v != '\0' && parse_threshold(v, &n) < 0) {
@@ -195,7 +200,8 @@ int64_t
 bjxa_hip_offload_threshold(int direction, int64_t eblocks)
 {
 	if (direction != BJXA_HIP_OFFLOAD_DECODE &&
-	    direction != BJXA_HIP_OFFLOAD_ENCODE) {
+	    direction != BJXA_HIP_OFFLOAD_ENCODE &&
+	    direction != BJXA_HIP_OFFLOAD_ENCODE_ADAPTIVE) {
 		errno = EINVAL;
 		return (-1);
 	}
@@ -205,6 +211,27 @@ bjxa_hip_offload_threshold(int direction, int64_t eblocks)
 		    __ATOMIC_RELAXED));
 	return ((int64_t)__atomic_exchange_n(&offload_min[direction],
 	    (uint64_t)eblocks, __ATOMIC_RELAXED));
+}
+
+/*
+ * Adaptive encode of a whole stream in host memory (LIBBJXA_HIP_0.5;
+ * algorithm DESIGN.md §3 "Adaptive encode").  Both routes write the same
+ * bytes.
+ */
+int
+bjxa_hip_encode_adaptive(const void *pcm, uint64_t frames, unsigned bits,
+    unsigned channels, uint32_t sync, void *xa)
+{
+	if (pcm == NULL || xa == NULL || frames == 0 ||
+	    (bits != 4 && bits != 6 && bits != 8) ||
+	    (channels != 1 && channels != 2) || sync == 0 ||
+	    frames > 32 * (uint64_t)0xffffffffu)
+		FAIL(EINVAL);
+	if (on_gpu(BJXA_HIP_OFFLOAD_ENCODE_ADAPTIVE, (frames + 31) / 32))
+		return (bjxa__gpu_encode_adaptive(pcm, frames, bits, channels,
+		    sync, xa));
+	return (bjxa__cpu_encode_adaptive(pcm, frames, bits, channels, sync,
+	    xa));
 }
 
 /* ---- objects (src/libbjxa.c:246-282) --------------------------------- */

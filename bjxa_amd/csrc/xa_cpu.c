@@ -240,3 +240,103 @@ bjxa__cpu_encode(const void *src, uint64_t frames, unsigned bits, unsigned ch,
 	}
 	return 0;
 }
+
+/* ---- adaptive encode (LIBBJXA_HIP_0.5) --------------------------------- */
+
+/*
+ * One candidate (predictor f, range r) over the 32 samples of a channel
+ * block, closed loop from the entry state: the codes q, the exit state and
+ * the squared error of what a decoder will reproduce.  s = 16 - bits - r.
+ */
+static uint64_t
+adapt_try(const int32_t x[FRAMES], unsigned bits, unsigned f, unsigned s,
+    const int32_t st[2], int32_t q[FRAMES], int32_t out[2])
+{
+	const int32_t k0 = k_gain[f][0], k1 = k_gain[f][1];
+	const int32_t half = (1 << s) >> 1, step = 1 << s;
+	const int32_t lo = -(1 << (bits - 1)), hi = (1 << (bits - 1)) - 1;
+	int32_t p0 = st[0], p1 = st[1];
+	uint64_t sse = 0;
+	int i;
+
+	for (i = 0; i < FRAMES; i++) {
+		const int32_t pred = (p0 * k0 + p1 * k1) / 256;
+		int32_t v = (x[i] - pred + half) >> s;
+		int32_t y, e;
+
+		v = v < lo ? lo : v > hi ? hi : v;
+		y = clamp16(v * step + pred);
+		e = x[i] - y;
+		sse += (uint64_t)((int64_t)e * e);
+		q[i] = v;
+		p1 = p0;
+		p0 = y;
+	}
+	out[0] = p0;
+	out[1] = p1;
+	return sse;
+}
+
+/*
+ * bjxa_hip_encode_adaptive on the calling thread: per channel block the
+ * candidate (f in 0..4, r in 0..min(16 - bits, 11)) of least squared error,
+ * ties to the smallest f * (R + 1) + r; blocks with b % sync == 0 take f = 0
+ * only, so every run of `sync` blocks stands alone (DESIGN.md §3 "Adaptive
+ * encode").  Frames past `frames` encode as zero samples.  Cannot fail.
+ */
+int
+bjxa__cpu_encode_adaptive(const void *src, uint64_t frames, unsigned bits,
+    unsigned ch, uint32_t sync, void *dst)
+{
+	const uint8_t *in = src;
+	uint8_t *out = dst;
+	const unsigned bsz = bits * 4 + 1;
+	const unsigned rmax = 16 - bits < 11 ? 16 - bits : 11;
+	const uint32_t mask = (1u << bits) - 1u;
+	int32_t st[2][2] = { { 0, 0 }, { 0, 0 } };
+	uint32_t b;
+
+	for (b = 0; frames > 0; b++) {
+		const unsigned n = frames < FRAMES ? (unsigned)frames : FRAMES;
+		const unsigned nf = b % sync == 0 ? 1 : 5;
+		int16_t pcm[2 * FRAMES];
+		unsigned c, f, r, i;
+
+		if (n < FRAMES)
+			memset(pcm, 0, sizeof pcm);
+		memcpy(pcm, in, (size_t)n * 2u * ch);
+		for (c = 0; c < ch; c++) {
+			int32_t x[FRAMES], q[FRAMES], best_q[FRAMES];
+			int32_t ex[2], best_ex[2] = { 0, 0 };
+			uint64_t best = UINT64_MAX;
+			unsigned best_prof = 0;
+			uint16_t code[FRAMES];
+
+			for (i = 0; i < FRAMES; i++)
+				x[i] = pcm[i * ch + c];
+			for (f = 0; f < nf; f++)
+				for (r = 0; r <= rmax; r++) {
+					const uint64_t e = adapt_try(x, bits, f,
+					    16 - bits - r, st[c], q, ex);
+					if (e < best) {
+						best = e;
+						best_prof = f << 4 | r;
+						memcpy(best_q, q, sizeof q);
+						memcpy(best_ex, ex, sizeof ex);
+					}
+				}
+			/* pack() takes codes left-justified in 16 bits */
+			for (i = 0; i < FRAMES; i++)
+				code[i] = (uint16_t)(((uint32_t)best_q[i] & mask) <<
+				    (16 - bits));
+			out[0] = (uint8_t)best_prof;
+			pack(code, bits, out + 1);
+			out += bsz;
+			st[c][0] = best_ex[0];
+			st[c][1] = best_ex[1];
+		}
+		in += (size_t)n * 2u * ch;
+		frames -= n;
+	}
+	return 0;
+}

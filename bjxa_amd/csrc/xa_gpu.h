@@ -93,6 +93,19 @@ int bjxa__cpu_decode(const void *src, uint32_t eblocks, unsigned bits,
 int bjxa__cpu_encode(const void *src, uint64_t frames, unsigned bits,
     unsigned ch, void *dst);
 
+/*
+ * Adaptive encode (bjxa_hip_encode_adaptive) of a whole stream held in host
+ * memory: `frames` frames of `src` into ceil(frames/32) eblocks at `dst`,
+ * prediction restarting every `sync` channel blocks.  The GPU side
+ * (xa_adapt.hip) allocates, copies in, launches, copies out and
+ * synchronizes; 0 or -1/errno (ENODEV, ENOMEM, EIO).  The CPU side
+ * (xa_cpu.c) writes the same bytes on the calling thread and cannot fail.
+ */
+int bjxa__gpu_encode_adaptive(const void *src, uint64_t frames, unsigned bits,
+    unsigned ch, uint32_t sync, void *dst);
+int bjxa__cpu_encode_adaptive(const void *src, uint64_t frames, unsigned bits,
+    unsigned ch, uint32_t sync, void *dst);
+
 #ifdef __cplusplus
 }
 #endif

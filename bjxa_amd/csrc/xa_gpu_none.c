@@ -58,6 +58,15 @@ bjxa__gpu_encode_many(struct bjxa__enc_job *jobs, uint32_t n)
 }
 
 int
+bjxa__gpu_encode_adaptive(const void *src, uint64_t frames, unsigned bits,
+    unsigned ch, uint32_t sync, void *dst)
+{
+	(void)src, (void)frames, (void)bits, (void)ch, (void)sync, (void)dst;
+	errno = ENODEV;
+	return -1;
+}
+
+int
 bjxa__gpu_encode(struct bjxa__gpu *g, const void *src, uint64_t frames,
     unsigned bits, unsigned ch, void *dst)
 {

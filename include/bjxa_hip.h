@@ -211,6 +211,38 @@ int bjxa_hip_encode_files(const void *const *wav, const size_t *wav_len,
     const uint8_t *bits, void *const *xa, const size_t *xa_len,
     int *status, uint32_t n);
 
+/*
+ * Adaptive encode (LIBBJXA_HIP_0.5).  The reference encoder, and every entry
+ * above, writes profile 0 for each block and keeps the top `bits` bits of a
+ * sample.  These two search, per channel block, all five predictors and the
+ * ranges 0..min(16 - bits, 11) in a closed loop and keep the pair of least
+ * squared error, so the output is not byte-comparable with the reference
+ * encoder's, is never worse per block, and decodes with any XA decoder.
+ * Prediction restarts (predictor 0) every `sync` channel blocks, which is
+ * what lets the runs of one stream be searched in parallel; the XA header's
+ * entry-state fields stay zero.  The bytes are defined by DESIGN.md §3
+ * "Adaptive encode" and are the same on both routes.
+ *
+ * EINVAL: a NULL pointer, frames == 0, bad bits or channels, sync == 0, more
+ * than 2^32 - 1 eblocks, a misaligned device pointer; all checked before the
+ * device is needed.  ceil(frames/32) * channels * (bits*4 + 1) bytes are
+ * written and the PCM is read no further than the 16-byte piece holding its
+ * last sample.
+ */
+#define BJXA_HIP_ADAPTIVE_SYNC_DEFAULT 64
+/* device-resident: one launch on `stream`, no host sync; d_pcm 16-B aligned,
+ * d_xa 4-B; ENODEV without a GPU, EIO on launch failure */
+int bjxa_hip_encode_adaptive_async(const void *d_pcm, uint64_t frames,
+    unsigned bits, unsigned channels, uint32_t sync, void *d_xa, void *stream);
+/* host buffers, a whole stream per call: on the GPU when one is present and
+ * the stream has at least bjxa_hip_offload_threshold(2) eblocks (default 8,
+ * the measured crossover; environment BJXA_OFFLOAD_ENCODE_ADAPTIVE), else on
+ * the calling thread's CPU core; ENOMEM and EIO can come from the GPU route */
+int bjxa_hip_encode_adaptive(const void *pcm, uint64_t frames, unsigned bits,
+    unsigned channels, uint32_t sync, void *xa);
+/* third direction of bjxa_hip_offload_threshold */
+#define BJXA_HIP_OFFLOAD_ENCODE_ADAPTIVE 2
+
 /* library/kernels build identifier, e.g. "bjxa-mi355x gfx950 ..." */
 const char *bjxa_hip_version(void);
 
